@@ -17,6 +17,11 @@ N > 1: launched by torch.distributed.run, one rank per GPU; every step processes
        --dist-mode band|mirror times one of the exchange-free decompositions instead; --dist-impl torch uses the
        torch.distributed implementation of the driver (atlas_amd/dist_torch.py; also what the CPU tests of this file
        run over gloo).
+A plain run does only what the headline needs: set-up, W warm-up steps, ONE timed block of exactly K steps, the result line.
+    --full            also what the headline does not need, as before: three timed blocks (`--blocks`), the device's clocks
+                      during them, the box's bare MFMA / HBM rates, the CPU baseline with the full-field parity check against
+                      it, and for N > 1 the link probe and the decomposition that was not timed
+    --dump-outputs D  after the timed steps, what the last step returned to its caller as D/<name>.npy (dump_outputs)
 Prints ONE JSON line (rank 0)."""
 import argparse
 import json
@@ -47,6 +52,8 @@ FP64_MFMA_PEAK_TFLOPS = 78.6   # MI355X spec, dense fp64 matrix = 1024 SIMDs x 3
 HBM_PEAK_GBS = 8000.0          # MI355X_MICROARCH.md: 8 TB/s spec
 PARITY_TOL = 1e-12             # rel-RMS of the whole field against the CPU restatement (the reference's tests: 1e-13 against analytic
                                # fields at T63; at T1279 the two fp64 summation orders differ by ~1e-15)
+DUMP_VALUES = 1 << 22          # --dump-outputs: at most this many float64 values over all ranks (32 MiB)
+DUMP_SEED = 20251115
 
 
 KERNEL_SOURCES = ("legendre_kernel.hip", "fft_kernel.hip", "fft_kernel_pairs.hip", "fft_ct_rows.h", "fft_pair.h", "fft_device.h", "fft_core.h", "fft_plan.cpp",
@@ -198,6 +205,28 @@ def full_field_parity(tr, grid, sample_fields, field_ref, sp_ref, device):
             "points": int(grid.size()), "tolerance_rel_rms": PARITY_TOL, "ok": bool(rms <= PARITY_TOL),
             "against": "cpu_baseline's field (oracle/translocal_blas.py: per-m dgemm + per-row pocketfft c2r), same spectra, "
                        "every grid point of every level; metric compute_rms of test_transgeneral.cc:472-489"}
+
+
+def dump_outputs(outdir, gp, nf, rank, world):
+    """--dump-outputs: the grid-point fields the last timed step returned ([level][point], this rank's points) as float64.
+    Whole as <outdir>/gridpoints.npy (shape nf x points) when they fit in DUMP_VALUES / world values; otherwise the values at
+    a fixed sample of that many positions of the flat array -- sorted, drawn with DUMP_SEED, so the same for every run with the
+    same arguments -- as <outdir>/gridpoints_sample.npy.  N > 1: every rank writes its own, with the suffix _rank<r>."""
+    import numpy as np
+    import torch
+    os.makedirs(outdir, exist_ok=True)
+    flat = gp.reshape(-1)
+    budget = DUMP_VALUES // world
+    name = "gridpoints"
+    if flat.numel() <= budget:
+        arr = flat.cpu().numpy().reshape(nf, -1)
+    else:
+        idx = np.sort(np.random.default_rng(DUMP_SEED).integers(0, flat.numel(), budget))
+        arr = flat[torch.from_numpy(idx).to(flat.device)].cpu().numpy()
+        name += "_sample"
+    if world > 1:
+        name += f"_rank{rank}"
+    np.save(os.path.join(outdir, name + ".npy"), np.ascontiguousarray(arr, dtype=np.float64))
 
 
 def dry_run(args):
@@ -546,9 +575,14 @@ def main():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=10)
     ap.add_argument("--warmup", type=int, default=3)
-    ap.add_argument("--blocks", type=int, default=3,
+    ap.add_argument("--blocks", type=int, default=None,
                     help="timed blocks of exactly --steps steps each (barrier + synchronize on both sides of every block); `value` is "
-                         "the MEDIAN block, min / max are reported beside it under `repeats`")
+                         "the MEDIAN block, min / max are reported beside it under `repeats` (default: 1, with --full 3)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check what the headline does not need: three timed blocks, device clocks, the box's "
+                         "bare MFMA / HBM rates, CPU baseline + full-field parity, N > 1: link probe and the other decomposition")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last step computed to DIR/<name>.npy (float64, at most 32 MiB)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--cpu-sample-fields", type=int, default=NLEV,
                     help="levels of the transform the CPU baseline runs (default: all 137 -- the dgemm shapes of the real call)")
@@ -573,19 +607,25 @@ def main():
                     help="--dry-run: assumed one-directional rate of one xGMI link in GB/s (MI355X: 7 links x ~153 GB/s "
                          "aggregate per GPU on paper; RCCL send/recv between two GPUs has been seen at ~50 GB/s)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.blocks is None:
+        args.blocks = 3 if args.full else 1
     if args.dry_run:
         return dry_run(args)
+
+    if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
+        # `python bench.py --gpus N` without a launcher: start the ranks ourselves (one per GPU, rendezvous on 127.0.0.1 --
+        # the container's host name may not resolve); the ranks inherit stdout, so the contract (ONE JSON line, from rank 0)
+        # and the per-phase watchdog are those of a launched run.  Before torch and the library are loaded: the launcher
+        # replaces this process (os.execv), which must not have started the HIP runtime.
+        return self_launch(args.gpus)
 
     import numpy as np
     import torch
     import atlas_amd
     from helpers import red_spectra
 
-    if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
-        # `python bench.py --gpus N` without a launcher: start the ranks ourselves (one per GPU, rendezvous on 127.0.0.1 --
-        # the container's host name may not resolve); the ranks inherit stdout, so the contract (ONE JSON line, from rank 0)
-        # and the per-phase watchdog are those of a launched run
-        return self_launch(args.gpus)
     standin_transform()          # BENCH_TEST_STANDIN=1 only (tests/test_bench_logic.py)
     rank = int(os.environ.get("RANK", "0"))
     world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -746,9 +786,10 @@ def main():
             return float(t_.item())
 
         # ---- the exchange-free mirror bands (a northern band of rows and its mirror image per GPU), usable only if every
-        # rank reproduces, bit for bit, the same rows through the GPU-tested zonal-band crop path
+        # rank reproduces, bit for bit, the same rows through the GPU-tested zonal-band crop path; set up for the trial of
+        # `--dist-mode auto` or, with --full, to be timed beside the headline
         dm, gp_m, mirror_ok = None, None, False
-        if world > 1 and dtr.mode == "alltoall" and not args.no_alt:
+        if world > 1 and dtr.mode == "alltoall" and not args.no_alt and (args.dist_mode == "auto" or args.full):
             wd.phase("mirror-band decomposition: set-up and bitwise self-check")
             ok = 0
             try:
@@ -784,7 +825,7 @@ def main():
         # -- and the line says which and why; the other one is reported as `alt_decomposition`.  The model (per-rank stage costs
         # measured in the trial, busiest pair's bytes, link rate from --xgmi-gbs or the all-pairs probe) is printed beside it.
         timed_mode, auto_choice, links = dtr.mode, None, None
-        if on_gpu and world > 1:
+        if on_gpu and world > 1 and args.full:
             try:
                 wd.phase("link probe (all pairs at once)")
                 links = link_probe(world, DEVICE)
@@ -816,7 +857,9 @@ def main():
                            "why": (f"trial: m-sharded Legendre + RCCL transposition {t_a2a:.2f} ms per step, mirror bands {t_mir:.2f} ms; "
                                    f"model: {model['why']}"),
                            "model": model,
-                           "link_rate_source": "--xgmi-gbs" if args.xgmi_gbs is not None else "all-pairs probe of this run"}
+                           "link_rate_source": "--xgmi-gbs" if args.xgmi_gbs is not None else (
+                               "all-pairs probe of this run" if (links or {}).get("gbs_per_pair_and_direction") else
+                               "assumed 50 GB/s: no link probe in this run (--full runs it)")}
         if auto_choice is not None and timed_mode == "mirror":
             tr, gp = dm.trans, gp_m
             step = step_mirror
@@ -831,7 +874,7 @@ def main():
     # `--blocks` blocks of exactly `--steps` steps, each bracketed by barrier + synchronize; the block with the MEDIAN time is
     # the one `value`, `ms_per_step` and the per-stage times describe (reference benchmark: min / max / iterations,
     # atlas-benchmark-trans.cc:257-289).  The device state is sampled while the blocks run.
-    sampler = DeviceSampler(local_rank) if (on_gpu and rank == 0) else None
+    sampler = DeviceSampler(local_rank) if (on_gpu and rank == 0 and args.full) else None
     state_before = sampler.snapshot() if sampler else None
     blocks = []
     if sampler:
@@ -857,6 +900,8 @@ def main():
     if sampler:
         sampler.stop()
     state_after = sampler.snapshot() if sampler else None
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, gp, nf, rank, world)
     order = sorted(range(len(blocks)), key=lambda i: blocks[i][0])
     dt, tm = blocks[order[(len(blocks) - 1) // 2]]   # the median block (the lower one of an even count)
     xt = xt_blocks[order[(len(blocks) - 1) // 2]]
@@ -869,7 +914,7 @@ def main():
     if use_dist and world > 1:
         import torch.distributed as dist
         # the decomposition that was NOT timed, for comparison (same steps, barriers, MAX over ranks), in a short run
-        if dtr.mode == "alltoall" and not args.no_alt:
+        if dtr.mode == "alltoall" and not args.no_alt and args.full:
             other = "mirror" if timed_mode == "alltoall" else "alltoall"
             alt = {"mode": other}
             if other == "mirror":
@@ -932,7 +977,7 @@ def main():
              "achieved": fft_gbs, "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": fft_gbs / HBM_PEAK_GBS,
              "avg_ms": fft_ms, "traffic": traffic.get("fourier_stage")},
         ]
-        if world == 1 and not use_dist:
+        if world == 1 and not use_dist and args.full:
             # what the part sustains on fp64 MFMA alone, measured right after the timed region (same thermal state)
             try:
                 from atlas_amd import _lib
@@ -1034,7 +1079,7 @@ def main():
         if os.environ.get("BENCH_TEST_STANDIN") == "1":
             out["metric"] = "STAND-IN TRANSFORM (driver-logic test over gloo, not a measurement): " + out["metric"]
             out["test_standin"] = True
-        if world == 1 and not use_dist and not args.no_cpu_baseline:
+        if world == 1 and not use_dist and args.full and not args.no_cpu_baseline:
             out["cpu_baseline"], field_ref, sp_ref = cpu_baseline_blas(args.cpu_sample_fields, keep_field=True)
             # full-field parity of the transform that was just timed against the field the CPU baseline computed (default:
             # all 137 levels of the same synthetic spectra): a fast kernel whose results differ is not a result

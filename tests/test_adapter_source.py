@@ -1,7 +1,9 @@
 """Source-level check of adapter/TransMI355X.cc (the TransImpl subclass a maintainer builds against an installed Atlas;
 it cannot be compiled in this image): (1) every pure virtual of the reference's TransImpl
 (src/atlas/trans/detail/TransImpl.h:38-191) has an override in the adapter with the same name and the same parameter
-types, (2) every atlas_amd__ symbol the adapter calls is declared in include/atlas_amd.h and exported by the library."""
+types, (2) every atlas_amd__ symbol the adapter calls is declared in include/atlas_amd.h and exported by the library.
+The reference's interfaces are read from tests/golden/adapter_interface.json (tests/golden/make_adapter_interface_fixture.py)."""
+import json
 import os
 import re
 
@@ -10,7 +12,19 @@ import pytest
 from atlas_amd import _lib
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-REF = "/root/reference/src/atlas/trans/detail/TransImpl.h"
+PURE_VIRTUAL = r"virtual\s+[^;{}()]*?\b([A-Za-z_0-9]+)\s*\(([^;{}]*?)\)\s*const\s*=\s*0\s*;"
+HALO_EXECUTE = (r"template\s*<typename DATA_TYPE, int RANK, typename ParallelDim = array::FirstDim>\s*void\s+%s"
+                r"\(array::Array& field, bool on_device = false\) const")
+
+
+def _interface(name):
+    """what tests/golden/adapter_interface.json records of the reference class `name`"""
+    with open(os.path.join(ROOT, "tests", "golden", "adapter_interface.json")) as f:
+        return json.load(f)[name]
+
+
+def _pure_virtuals(name):
+    return {(m, tuple(params)) for m, params in _interface(name)}
 
 
 def _norm_params(text):
@@ -53,11 +67,8 @@ def test_every_atlas_amd_symbol_of_the_adapter_exists():
         assert hasattr(_lib.lib, sym), f"{sym} not exported by libatlas_amd.so"
 
 
-@pytest.mark.skipif(not os.path.exists(REF), reason="the reference checkout is only present in the build container")
 def test_adapter_overrides_every_pure_virtual_of_TransImpl():
-    ref = open(REF).read()
-    ref = ref[ref.index("class TransImpl"):]
-    pure = _methods(ref, r"virtual\s+[^;{}()]*?\b([A-Za-z_0-9]+)\s*\(([^;{}]*?)\)\s*const\s*=\s*0\s*;")
+    pure = _pure_virtuals("TransImpl")
     assert len(pure) >= 28, len(pure)
     src = _adapter("TransMI355X.cc")
     hdr = _adapter("TransMI355X.h")
@@ -68,17 +79,10 @@ def test_adapter_overrides_every_pure_virtual_of_TransImpl():
     assert re.search(r'TransBuilderGrid<TransMI355X>\s+builder\("mi355x",\s*"mi355x"\)', src)
 
 
-REF_TRANS = "/root/reference/src/atlas/trans"
-needs_ref = pytest.mark.skipif(not os.path.exists(REF), reason="the reference checkout is only present in the build container")
-
-
-@needs_ref
 def test_adapter_registers_vordivtouv_and_overrides_its_interface():
     """VorDivToUVImpl (VorDivToUV.h:36-62): truncation() and execute(nb_coeff, nb_fields, vor, div, U, V, config); the builder
     template needs constructors (FunctionSpace, config) and (int, config) (VorDivToUV.h:96-104)"""
-    ref = open(os.path.join(REF_TRANS, "VorDivToUV.h")).read()
-    ref = ref[ref.index("class VorDivToUVImpl"):ref.index("class VorDivToUVFactory")]
-    pure = _methods(ref, r"virtual\s+[^;{}()]*?\b([A-Za-z_0-9]+)\s*\(([^;{}]*?)\)\s*const\s*=\s*0\s*;")
+    pure = _pure_virtuals("VorDivToUVImpl")
     assert {m[0] for m in pure} == {"truncation", "execute"}
     src = _adapter("VorDivToUVMI355X.cc")
     mine = _methods(src, r"\b([A-Za-z_0-9]+)\s*\(([^;{}]*?)\)\s*const\s*override")
@@ -87,13 +91,10 @@ def test_adapter_registers_vordivtouv_and_overrides_its_interface():
     assert re.search(r"VorDivToUVMI355X\(const FunctionSpace&", src) and re.search(r"VorDivToUVMI355X\(int truncation", src)
 
 
-@needs_ref
 def test_adapter_registers_legendre_cache_creator_and_overrides_its_interface():
     """LegendreCacheCreatorImpl (LegendreCacheCreator.h:30-44): supported, uid, create(path), create(), estimate; the
     builder constructs T(grid, truncation, config) (LegendreCacheCreator.h:98-105)"""
-    ref = open(os.path.join(REF_TRANS, "LegendreCacheCreator.h")).read()
-    ref = ref[ref.index("class LegendreCacheCreatorImpl"):ref.index("class LegendreCacheCreator :")]
-    pure = _methods(ref, r"virtual\s+[^;{}()]*?\b([A-Za-z_0-9]+)\s*\(([^;{}]*?)\)\s*const\s*=\s*0\s*;")
+    pure = _pure_virtuals("LegendreCacheCreatorImpl")
     assert {m[0] for m in pure} == {"supported", "uid", "create", "estimate"} and len(pure) == 5
     src = _adapter("LegendreCacheCreatorMI355X.cc")
     mine = _methods(src, r"\b([A-Za-z_0-9]+)\s*\(([^;{}]*?)\)\s*const\s*override")
@@ -105,11 +106,9 @@ def test_adapter_registers_legendre_cache_creator_and_overrides_its_interface():
     assert "export_legendre_" in src and 'getBool("export_legendre"' in trans and 'getString("write_legendre"' in trans
 
 
-@needs_ref
 def test_adapter_halo_exchange_has_the_public_surface_of_parallel_HaloExchange():
     """HaloExchange.h:37-58: constructors, name(), four setup overloads, execute / execute_adjoint templates"""
-    ref = open("/root/reference/src/atlas/parallel/HaloExchange.h").read()
-    ref = ref[ref.index("class HaloExchange"):ref.index("private:  // methods")]
+    ref = _interface("HaloExchange")
     src = _adapter("HaloExchangeMI355X.h")
     mine = src[src.index("class HaloExchangeMI355X"):src.index("private:")]
 
@@ -118,11 +117,10 @@ def test_adapter_halo_exchange_has_the_public_surface_of_parallel_HaloExchange()
         for m in re.finditer(r"void\s+setup\(([^)]*)\)", text):
             out.add(_norm_params(m.group(1)))
         return out
-    assert len(setups(ref)) == 4 and setups(ref) == setups(mine)
+    ref_setups = {tuple(params) for params in ref["setup"]}
+    assert len(ref_setups) == 4 and ref_setups == setups(mine)
     for name in ("execute", "execute_adjoint"):
-        pat = r"template\s*<typename DATA_TYPE, int RANK, typename ParallelDim = array::FirstDim>\s*void\s+" + name + \
-              r"\(array::Array& field, bool on_device = false\) const"
-        assert re.search(pat, ref) and re.search(pat, mine), name
+        assert name in ref["execute_templates"] and re.search(HALO_EXECUTE % name, mine), name
     assert re.search(r"const std::string& name\(\) const", mine)
     assert re.search(r"HaloExchangeMI355X\(const std::string& name\)", mine) and re.search(r"HaloExchangeMI355X\(\)", mine)
     # the two collectives and the point-to-point calls of the reference are the adapter's as well
@@ -179,19 +177,25 @@ def test_adapter_compiles_against_an_installed_atlas(tmp_path):
         assert r.returncode == 0, f"{os.path.basename(src)} {extra}:\n{r.stderr[-4000:]}"
 
 
-REF_SRC = "/root/reference/src"
 STUBS = os.path.join(ROOT, "tools", "adapter_stubs")
 
 
-def _front_end(src, extra=()):
-    import subprocess
-    cmd = ["g++", "-std=c++17", "-fsyntax-only", "-Wall", "-Woverloaded-virtual", *extra, "-I", REF_SRC, "-I", "/root/reference/pluto/src",
-           "-I", os.path.join(ROOT, "include"), "-I", os.path.join(ROOT, "adapter"), "-I", STUBS, src]
-    return subprocess.run(cmd, capture_output=True, text=True)
+def _reference_build():
+    """what build() compiled of adapter/ against the reference's headers (oracle/adapter_ref.py): manifest + objects"""
+    from oracle import adapter_ref
+    path = os.path.join(adapter_ref.OUT, "manifest.json")
+    if not os.path.exists(path):
+        pytest.skip("oracle/_ref/adapter/ not built: build() compiles it where the reference's source checkout is present "
+                    "(oracle/adapter_ref.py)")
+    with open(path) as f:
+        m = json.load(f)
+    assert m["digest"] == adapter_ref.digest(), "oracle/_ref/adapter/ was built from other sources: run build() again"
+    names = [name for name, _, _ in adapter_ref.jobs()]
+    assert sorted(m["jobs"]) == sorted(names) and len(adapter_ref.units()) >= 4
+    return m, adapter_ref.OUT
 
 
-@pytest.mark.skipif(not os.path.isdir(REF_SRC), reason="the reference checkout is only present in the build container")
-def test_adapter_passes_a_compiler_front_end_against_the_reference_headers(tmp_path):
+def test_adapter_passes_a_compiler_front_end_against_the_reference_headers():
     """[r5] VERDICT r4 item 7: every adapter translation unit through g++'s front end against the reference's REAL headers
     (src/atlas/trans/detail/TransImpl.h:38-191, VorDivToUV.h, LegendreCacheCreator.h, library/Plugin.h, array/*, parallel/mpi/mpi.h)
     -- the 28 `override`s, const-ness, default arguments, make_device_view deduction, REGISTER_LIBRARY -- with tools/adapter_stubs/
@@ -200,34 +204,28 @@ def test_adapter_passes_a_compiler_front_end_against_the_reference_headers(tmp_p
     First run of this check found three defects regular expressions could not see: IterateLonLat used through a forward
     declaration (TransMI355X.cc), array::get_parallel_dim without its header and a most-vexing-parse in the RCCL transport
     (HaloExchangeMI355X.h)."""
-    units = [os.path.join(ROOT, "adapter", f) for f in sorted(os.listdir(os.path.join(ROOT, "adapter"))) if f.endswith(".cc")]
-    assert len(units) >= 4
-    halo = os.path.join(STUBS, "check_halo_exchange.cc")       # instantiates execute / execute_adjoint for 4 types x ranks 1-3
-    jobs = [(u, ()) for u in units] + [(halo, ()), (halo, ("-DATLAS_AMD_HALO_TRANSPORT_RCCL",))]
-    for src, extra in jobs:
-        r = _front_end(src, extra)
-        assert r.returncode == 0, f"{os.path.basename(src)} {extra}:\n{r.stderr[-4000:]}"
-        own = [ln for ln in r.stderr.splitlines() if "warning" in ln and ("/adapter/" in ln.split(":")[0] or ln.startswith("adapter/"))]
+    m, _ = _reference_build()
+    # the adapter units, and check_halo_exchange.cc (execute / execute_adjoint for 4 types x ranks 1-3) in both transports
+    for name, job in m["jobs"].items():
+        r = job["front_end"]
+        assert r["rc"] == 0, f"{name} {job['extra']}:\n{r['stderr'][-4000:]}"
+        own = [ln for ln in r["stderr"].splitlines() if "warning" in ln and ("/adapter/" in ln.split(":")[0] or ln.startswith("adapter/"))]
         assert not own, own
     # the check has teeth: an override whose signature drifts from TransImpl.h (a dropped const) is rejected by the same command
-    bad = tmp_path / "drift.cc"
-    bad.write_text('#include "TransMI355X.h"\n'
-                   "struct Drift : atlas::trans::TransMI355X {\n"
-                   "    using TransMI355X::TransMI355X;\n"
-                   "    int truncation() override { return 0; }\n"      # TransImpl::truncation() is const
-                   "};\n")
-    r = _front_end(str(bad))
-    assert r.returncode != 0 and "override" in r.stderr
+    assert m["drift"]["rc"] != 0 and "override" in m["drift"]["stderr"]
 
 
 def test_adapter_stubs_are_not_used_by_the_product():
     """tools/adapter_stubs/ is test infrastructure for the check above: nothing under atlas_amd/, include/, adapter/ or oracle/
-    includes from it, and it holds no reference source (only generated-header stand-ins and eckit declarations)"""
+    includes from it -- except oracle/adapter_ref.py, which runs that check --, and it holds no reference source (only
+    generated-header stand-ins and eckit declarations)"""
     for top in ("atlas_amd", "include", "adapter", "oracle"):
         for dp, _, fs in os.walk(os.path.join(ROOT, top)):
-            if "/build" in dp or "__pycache__" in dp:
+            if "/build" in dp or "__pycache__" in dp or "/_ref" in dp:
                 continue
             for f in fs:
+                if os.path.join(dp, f) == os.path.join(ROOT, "oracle", "adapter_ref.py"):
+                    continue
                 if f.endswith((".h", ".hpp", ".cc", ".cpp", ".hip", ".c", ".py", ".txt", ".cmake")) or f == "Makefile":
                     txt = open(os.path.join(dp, f), errors="replace").read()
                     assert "adapter_stubs" not in txt, os.path.join(dp, f)
@@ -238,8 +236,7 @@ def test_adapter_stubs_are_not_used_by_the_product():
                              "pluto/pluto_config.h", "README.md", "check_halo_exchange.cc")) for n in names), names
 
 
-@pytest.mark.skipif(not os.path.isdir(REF_SRC), reason="the reference checkout is only present in the build container")
-def test_adapter_compiles_to_objects_and_defines_the_three_static_builders(tmp_path):
+def test_adapter_compiles_to_objects_and_defines_the_three_static_builders():
     """[r6] VERDICT r5 item 8: one step past the front end -- every adapter translation unit compiled to an OBJECT (g++ -c) against
     the reference's real headers + the stand-in declarations, so that the templates are instantiated and code is generated
     (array::make_device_view<double, 1>, TransBuilderGrid<TransMI355X>, VorDivToUVBuilder<..>, LegendreCacheCreatorBuilder<..>,
@@ -248,18 +245,14 @@ def test_adapter_compiles_to_objects_and_defines_the_three_static_builders(tmp_p
     constructors are referenced, the plugin object registers itself, and the only undefined atlas_amd__ symbols are ones
     libatlas_amd.so exports.  Still not a link against Atlas (no eckit in the image): f1 stays partial (tools/adapter_ci.md)."""
     import subprocess
-    units = [os.path.join(ROOT, "adapter", f) for f in sorted(os.listdir(os.path.join(ROOT, "adapter"))) if f.endswith(".cc")]
-    halo = os.path.join(STUBS, "check_halo_exchange.cc")
+    m, outdir = _reference_build()
     objs = {}
-    for src, extra in [(u, ()) for u in units] + [(halo, ()), (halo, ("-DATLAS_AMD_HALO_TRANSPORT_RCCL",))]:
-        out = tmp_path / (os.path.basename(src).replace(".cc", "") + ("_rccl" if extra else "") + ".o")
-        cmd = ["g++", "-std=c++17", "-O0", "-fPIC", "-c", "-Wall", *extra, "-I", REF_SRC, "-I", "/root/reference/pluto/src",
-               "-I", os.path.join(ROOT, "include"), "-I", os.path.join(ROOT, "adapter"), "-I", STUBS, src, "-o", str(out)]
-        r = subprocess.run(cmd, capture_output=True, text=True)
-        assert r.returncode == 0, f"{os.path.basename(src)} {extra}:\n{r.stderr[-4000:]}"
-        nm = subprocess.run(["nm", "-C", str(out)], capture_output=True, text=True)
+    for name, job in m["jobs"].items():
+        r = job["object"]
+        assert r["rc"] == 0, f"{name} {job['extra']}:\n{r['stderr'][-4000:]}"
+        nm = subprocess.run(["nm", "-C", os.path.join(outdir, name + ".o")], capture_output=True, text=True)
         assert nm.returncode == 0
-        objs[out.name] = nm.stdout
+        objs[name + ".o"] = nm.stdout
     t = objs["TransMI355X.o"]
     # the static builder object (a data symbol of the unit) and the factory's constructor it runs at load time
     assert re.search(r"\b[bBdD] .*builder", t), "no static builder object in TransMI355X.o"

@@ -34,6 +34,13 @@ def _bench_worker(rank, world, port, argv, grid, corrupt_mirror, outdir):
     import bench
     from fake_trans import FakeTrans
     FakeTrans.corrupt_mirror = corrupt_mirror
+    calls = [0]                 # every call of the single-device entry point, timed or not (run_bench: invtrans_calls_<rank>)
+    invtrans = FakeTrans.invtrans
+
+    def counted(self, *a):
+        calls[0] += 1
+        return invtrans(self, *a)
+    FakeTrans.invtrans = counted
     atlas_amd.Trans = FakeTrans
     aadist.Trans = FakeTrans
     aadist.DEVICE = "cpu"
@@ -45,6 +52,8 @@ def _bench_worker(rank, world, port, argv, grid, corrupt_mirror, outdir):
         bench.main()
     finally:
         sys.stdout.flush()
+        with open(os.path.join(outdir, f"invtrans_calls_{rank}.txt"), "w") as f:
+            f.write(str(calls[0]))
 
 
 def run_bench(tmp_path, world, argv, grid="O16", corrupt_mirror=False, expect_value=True):
@@ -73,7 +82,7 @@ def run_bench(tmp_path, world, argv, grid="O16", corrupt_mirror=False, expect_va
 
 
 def test_single_gpu_line_has_roofline_and_cpu_baseline(tmp_path):
-    out = run_bench(tmp_path, 1, ["--gpus", "1", "--steps", "2", "--warmup", "1", "--cpu-sample-fields", "2"])
+    out = run_bench(tmp_path, 1, ["--gpus", "1", "--steps", "2", "--warmup", "1", "--cpu-sample-fields", "2", "--full"])
     assert out["steps"] == 2 and out["warmup"] == 1
     assert out["config"]["parallelism"] == "single GPU"
     cb = out["cpu_baseline"]
@@ -93,6 +102,49 @@ def test_single_gpu_line_has_roofline_and_cpu_baseline(tmp_path):
     par = out["parity"]
     assert par["fields"] == 2 and par["rows"] == 32 and par["points"] > 0 and par["tolerance_rel_rms"] == 1e-12
     assert set(par) >= {"rel_rms", "max_abs", "ok", "against"}
+    # transforms run: 1 warm-up + 3 blocks x 2 steps + the parity call
+    assert int(open(tmp_path / "invtrans_calls_0.txt").read()) == 1 + 3 * 2 + 1
+
+
+def test_plain_single_gpu_run_times_exactly_the_requested_steps_and_dumps_its_outputs(tmp_path):
+    """without --full: one timed block of exactly --steps steps and nothing the headline does not need; --dump-outputs writes
+    the grid-point fields of the last timed step, the same in two runs with the same arguments"""
+    import numpy as np
+    outs = []
+    for i in range(2):
+        run_dir = tmp_path / f"run{i}"
+        run_dir.mkdir()
+        out = run_bench(run_dir, 1, ["--gpus", "1", "--steps", "3", "--warmup", "1", "--dump-outputs", str(run_dir / "dump")])
+        assert out["steps"] == 3 and out["warmup"] == 1 and out["unit"] == "transforms/s"
+        assert out["repeats"]["blocks"] == 1 and out["repeats"]["steps_per_block"] == 3
+        assert out["ms_per_step"] == pytest.approx(out["repeats"]["ms_per_step"][0])
+        assert out["value"] == pytest.approx(1e3 / out["ms_per_step"])
+        assert out["clocks"] is None and "cpu_baseline" not in out and "parity" not in out
+        assert out["box"] == {"mfma_f64_sustained_tflops": None, "hbm_copy_gbs": None}
+        # the transform ran exactly warm-up + steps times: nothing else in a plain run calls it
+        assert int(open(run_dir / "invtrans_calls_0.txt").read()) == 1 + 3
+        files = sorted(os.listdir(run_dir / "dump"))
+        assert files == ["gridpoints.npy"]
+        gp = np.load(run_dir / "dump" / "gridpoints.npy")
+        assert gp.dtype == np.float64 and gp.shape[0] == 3 and np.isfinite(gp).all() and np.abs(gp).max() > 0
+        outs.append(gp)
+    assert np.array_equal(outs[0], outs[1])
+
+
+def test_dump_of_a_large_output_is_a_fixed_sample_within_the_size_limit(tmp_path, monkeypatch):
+    import numpy as np
+    import torch
+    import bench
+    monkeypatch.setattr(bench, "DUMP_VALUES", 1000)
+    gp = torch.arange(3 * 700, dtype=torch.float64)
+    for d in ("a", "a2"):
+        bench.dump_outputs(str(tmp_path / d), gp, 3, 0, 1)
+    bench.dump_outputs(str(tmp_path / "b"), gp, 3, 1, 2)
+    s = np.load(tmp_path / "a" / "gridpoints_sample.npy")
+    assert s.dtype == np.float64 and s.shape == (1000,) and np.all(np.diff(s) >= 0) and s.max() < 2100
+    assert np.array_equal(s, np.load(tmp_path / "a2" / "gridpoints_sample.npy"))
+    r = np.load(tmp_path / "b" / "gridpoints_sample_rank1.npy")
+    assert r.shape == (500,)
 
 
 def test_gpus_n_without_a_launcher_starts_its_own_ranks(tmp_path):
@@ -117,6 +169,8 @@ def test_gpus_n_without_a_launcher_starts_its_own_ranks(tmp_path):
     assert out["metric"].startswith("STAND-IN")
     assert out["config"]["parallelism"].startswith(("m-sharded", "mirror-band"))       # --dist-mode auto: the trial's winner
     assert out["multi_gpu_crosscheck"]["bitwise_equal_on_all_ranks"] is True
+    # no link probe without --full (nor off the GPU): the model's link rate is the assumed one, and the line says so
+    assert out["auto_choice"]["link_rate_source"].startswith("assumed 50 GB/s") and out["auto_choice"]["model"]["link_gbs"] == 50.0
 
 
 def test_a_launcher_with_the_wrong_rank_count_is_an_error(tmp_path):
@@ -148,7 +202,7 @@ def check_auto_line(out, world):
 
 
 def test_two_ranks_auto_times_the_winner_of_a_trial_and_reports_the_other_beside_it(tmp_path):
-    out = run_bench(tmp_path, 2, ["--gpus", "2", "--steps", "2", "--warmup", "1"])
+    out = run_bench(tmp_path, 2, ["--gpus", "2", "--steps", "2", "--warmup", "1", "--full"])
     check_auto_line(out, 2)
     assert out["dist_impl"].startswith("torch")                           # off the GPU; "native" on MI355X
     assert "cpu_baseline" not in out                                      # rank 0 at N = 1 only
@@ -184,7 +238,7 @@ def test_the_model_of_auto_picks_mirror_bands_where_the_exchange_does_not_hide()
 
 
 def test_mirror_bands_are_not_reported_when_their_self_check_fails(tmp_path):
-    out = run_bench(tmp_path, 2, ["--gpus", "2", "--steps", "1", "--warmup", "0"], corrupt_mirror=True)
+    out = run_bench(tmp_path, 2, ["--gpus", "2", "--steps", "1", "--warmup", "0", "--full"], corrupt_mirror=True)
     assert out["config"]["parallelism"].startswith("m-sharded")
     assert out["alt_decomposition"]["selfcheck_bitwise_equal_on_all_ranks"] is False
     assert "value" not in out["alt_decomposition"]
@@ -218,7 +272,7 @@ def test_explicit_modes(tmp_path):
 
 
 def test_eight_ranks_auto(tmp_path):
-    out = run_bench(tmp_path, 8, ["--gpus", "8", "--steps", "1", "--warmup", "1"], grid="O32")
+    out = run_bench(tmp_path, 8, ["--gpus", "8", "--steps", "1", "--warmup", "1", "--full"], grid="O32")
     assert out["n_gpus"] == 8
     check_auto_line(out, 8)
     assert "8 transform(s) per step" in out["config"]["workload"]

@@ -17,7 +17,9 @@ except Exception as e:
     print('   smi unavailable', e)"; }
 for rep in $(seq $REPS); do for tree in "$@"; do
   smi
-  ( cd "$tree" && python bench.py --steps $STEPS --warmup 3 --no-cpu-baseline 2>/dev/null ) | python3 -c "
+  # the bare-MFMA rate printed below is measured only with --full where bench.py has that option (older trees: always)
+  full=""; grep -q -- '"--full"' "$tree/bench.py" && full=--full
+  ( cd "$tree" && python bench.py --steps $STEPS --warmup 3 --no-cpu-baseline $full 2>/dev/null ) | python3 -c "
 import json, sys
 for ln in sys.stdin.read().strip().splitlines():
     if not ln.startswith('{'):

@@ -22,5 +22,5 @@ tail -40 $O/summary.txt
 # the default bench LAST, with this run's PMC profile in place (profiles/rNN_pmc_traffic.json of the round, stamped with the digest
 # of the kernel sources): the line then carries `traffic` from the counters of the same sources on the same box
 cp $O/pmc_traffic.json profiles/${PROF_ROUND_TAG:-r03}_pmc_traffic.json
-( time python bench.py ) > $O/bench_default.json 2> $O/bench_default.err
+( time python bench.py --full ) > $O/bench_default.json 2> $O/bench_default.err
 tail -c 400 $O/bench_default.json
