@@ -125,6 +125,10 @@ TransMI355X::TransMI355X(const Cache& cache, const Grid& grid, const Domain& dom
             ATLAS_ASSERT(gs.nx(j) == cnt[j], "longitude window of the crop differs from Grid(grid, domain)");
         }
     }
+    dirtrans_ = config.getBool("dirtrans", false);   // the direct transform (an extension; the library refuses what it does not support)
+    if (dirtrans_) {
+        cfg += std::string(cfg.empty() ? "" : ";") + "dirtrans=1";
+    }
     const void* blob = cache.legendre() ? cache.legendre().data() : nullptr;   // trans/Cache.h:98-136
     const size_t len = cache.legendre() ? cache.legendre().size() : 0;
     handle_.reset(atlas_amd__Trans__new_config(agrid_.get(), truncation_, cfg.c_str(), blob, len));
@@ -221,6 +225,36 @@ void TransMI355X::invtrans(const FieldSet& spfields, FieldSet& gpfields, const e
     ATLAS_ASSERT(spfields.size() == gpfields.size());   // TransLocal.cc:838-844
     for (idx_t f = 0; f < spfields.size(); ++f) {
         invtrans(spfields[f], gpfields[f], config);
+    }
+}
+
+void TransMI355X::dirtrans(const int nb_fields, const double scalar_fields[], double scalar_spectra[],
+                           const eckit::Configuration&) const {
+    if (!dirtrans_ || regional_) {
+        ATLAS_NOTIMPLEMENTED;
+    }
+    check(atlas_amd__Trans__dirtrans_scalar(handle_.get(), nb_fields, scalar_fields, scalar_spectra));
+}
+
+// rank-1 fields, the shape rules of invtrans(Field, Field)
+void TransMI355X::dirtrans(const Field& gpfield, Field& spfield, const eckit::Configuration& config) const {
+    if (!dirtrans_ || regional_) {
+        ATLAS_NOTIMPLEMENTED;
+    }
+    ATLAS_ASSERT(gpfield.rank() == 1, "Only rank-1 fields supported at the moment");
+    ATLAS_ASSERT(spfield.rank() == 1, "Only rank-1 fields supported at the moment");
+    const auto gp = array::make_view<double, 1>(gpfield);
+    auto sp       = array::make_view<double, 1>(spfield);
+    dirtrans(1, gp.data(), sp.data(), config);
+}
+
+void TransMI355X::dirtrans(const FieldSet& gpfields, FieldSet& spfields, const eckit::Configuration& config) const {
+    if (!dirtrans_ || regional_) {
+        ATLAS_NOTIMPLEMENTED;
+    }
+    ATLAS_ASSERT(gpfields.size() == spfields.size());
+    for (idx_t f = 0; f < gpfields.size(); ++f) {
+        dirtrans(gpfields[f], spfields[f], config);
     }
 }
 

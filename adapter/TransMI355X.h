@@ -50,13 +50,14 @@ public:
     void invtrans(const int nb_vordiv_fields, const double vorticity_spectra[], const double divergence_spectra[],
                   double gp_fields[], const eckit::Configuration& = util::NoConfig()) const override;
 
+    // ---- direct transform of scalar fields: an extension, forwarded to the library when the configuration carries dirtrans=true
+    // (global Gaussian grids); otherwise ATLAS_NOTIMPLEMENTED, as TransLocal (TransLocal.cc:848-857,899-927)
+    void dirtrans(const Field& gpfield, Field& spfield, const eckit::Configuration& = util::NoConfig()) const override;
+    void dirtrans(const FieldSet& gpfields, FieldSet& spfields, const eckit::Configuration& = util::NoConfig()) const override;
+    void dirtrans(const int nb_fields, const double scalar_fields[], double scalar_spectra[],
+                  const eckit::Configuration& = util::NoConfig()) const override;
+
     // ---- ATLAS_NOTIMPLEMENTED in TransLocal as well (TransLocal.cc:848-857,899-927,1599-1685)
-    void dirtrans(const Field&, Field&, const eckit::Configuration& = util::NoConfig()) const override {
-        ATLAS_NOTIMPLEMENTED;
-    }
-    void dirtrans(const FieldSet&, FieldSet&, const eckit::Configuration& = util::NoConfig()) const override {
-        ATLAS_NOTIMPLEMENTED;
-    }
     void dirtrans_wind2vordiv(const Field&, Field&, Field&,
                               const eckit::Configuration& = util::NoConfig()) const override {
         ATLAS_NOTIMPLEMENTED;
@@ -104,9 +105,6 @@ public:
                       const eckit::Configuration& = util::NoConfig()) const override {
         ATLAS_NOTIMPLEMENTED;
     }
-    void dirtrans(const int, const double[], double[], const eckit::Configuration& = util::NoConfig()) const override {
-        ATLAS_NOTIMPLEMENTED;
-    }
     void dirtrans(const int, const double[], double[], double[],
                   const eckit::Configuration& = util::NoConfig()) const override {
         ATLAS_NOTIMPLEMENTED;
@@ -138,6 +136,7 @@ private:
     };
     Grid grid_;
     int truncation_;
+    bool dirtrans_ = false;   // built with dirtrans=true: the library object runs the direct transform
     functionspace::Spectral spectral_;
     // exactly one of handle_ / regional_ is set.  Owning pointers: a constructor that throws after the library objects
     // exist (an ATLAS_ASSERT on the crop, a failed cache export) releases them

@@ -106,6 +106,7 @@ Grid_nx = _sig("atlas_amd__Grid__nx", C.c_int, c_void_p, c_void_p)
 Grid_y = _sig("atlas_amd__Grid__y", C.c_int, c_void_p, c_void_p)
 Grid_crop_to_domain = _sig("atlas_amd__Grid__crop_to_domain", C.c_int, c_void_p, C.c_double, C.c_double, C.c_double, C.c_double,
                            C.POINTER(C.c_int), C.POINTER(C.c_int), c_void_p, c_void_p, C.c_int)
+Grid_gaussian_weights = _sig("atlas_amd__Grid__gaussian_weights", C.c_int, c_void_p, c_void_p)
 gaussian_latitudes_npole_spole = _sig("atlas_amd__gaussian_latitudes_npole_spole", C.c_int, C.c_int, c_void_p)
 
 Trans_new = _sig("atlas_amd__Trans__new", c_void_p, c_void_p, C.c_int)
@@ -130,6 +131,9 @@ Trans_invtrans_device_f32 = _sig("atlas_amd__Trans__invtrans_device_f32", C.c_in
                                  c_void_p, c_void_p, c_void_p)
 Trans_invtrans_scalar_f32 = _sig("atlas_amd__Trans__invtrans_scalar_f32", C.c_int, c_void_p, C.c_int, c_void_p, c_void_p)
 Trans_dirtrans_scalar = _sig("atlas_amd__Trans__dirtrans_scalar", C.c_int, c_void_p, C.c_int, c_void_p, c_void_p)
+Trans_dirtrans_scalar_device = _sig("atlas_amd__Trans__dirtrans_scalar_device", C.c_int, c_void_p, C.c_int, c_void_p,
+                                    c_void_p)
+Trans_timings_dirtrans = _sig("atlas_amd__Trans__timings_dirtrans", C.c_int, c_void_p, c_void_p, C.c_int)
 Trans_dirtrans_wind2vordiv = _sig("atlas_amd__Trans__dirtrans_wind2vordiv", C.c_int, c_void_p, C.c_int, c_void_p,
                                   c_void_p, c_void_p)
 Trans_invtrans_adj_scalar = _sig("atlas_amd__Trans__invtrans_adj_scalar", C.c_int, c_void_p, C.c_int, c_void_p,

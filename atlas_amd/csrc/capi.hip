@@ -330,6 +330,14 @@ int atlas_amd__Grid__y(const atlas_amd_Grid* g, double y_out[]) {
     std::memcpy(y_out, g->g.y.data(), sizeof(double) * g->g.y.size());
     return 0;
 }
+int atlas_amd__Grid__gaussian_weights(const atlas_amd_Grid* grid, double weights_out[]) {
+    AA_TRY
+    if (!grid || !weights_out) {
+        throw std::invalid_argument("Grid::gaussian_weights: null handle or NULL output");
+    }
+    grid::gaussian_weights(grid->g, weights_out);
+    AA_CATCH_INT
+}
 int atlas_amd__gaussian_latitudes_npole_spole(int N, double lats_out[]) {
     AA_TRY
     if (N < 1 || N > grid::kMaxGaussianN || !lats_out) {
@@ -437,6 +445,9 @@ atlas_amd_Trans* atlas_amd__Trans__new_config(const atlas_amd_Grid* grid, int tr
             }
             cfg.device_tables = kv.second == "device" ? 1 : 0;
         }
+        else if (kv.first == "dirtrans") {   // the direct transform (an extension: TransLocal does not implement it)
+            cfg.dirtrans = std::stoi(kv.second) != 0;
+        }
         else if (kv.first == "type") {
             // atlas option::type: this library IS the "local" implementation (TransLocal.cc:57)
             if (kv.second != "local" && kv.second != "mi355x") {
@@ -457,6 +468,9 @@ atlas_amd_Trans* atlas_amd__Trans__new_config(const atlas_amd_Grid* grid, int tr
         if (cfg.row_end > cfg.row_begin || legendre_cache) {
             throw std::invalid_argument("shard=mirror cannot be combined with rows= or a Legendre cache");
         }
+        if (cfg.dirtrans) {
+            throw std::invalid_argument("dirtrans: nparts > 1 (sharded objects) is not supported; use a single-device Trans");
+        }
         const std::vector<int> b = trans::mirror_bands(grid->g, cfg.nparts);
         if (cfg.part < 0 || cfg.part >= cfg.nparts) {
             throw std::invalid_argument("Trans: invalid (nparts, part)");
@@ -473,7 +487,11 @@ atlas_amd_Trans* atlas_amd__Trans__new_config(const atlas_amd_Grid* grid, int tr
         t->mirror_b0 = b0, t->mirror_b1 = b1;
         return t;
     }
-    return new atlas_amd_Trans{new trans::Trans(grid->g, truncation, cfg), grid};
+    std::unique_ptr<trans::Trans> impl(new trans::Trans(grid->g, truncation, cfg));
+    if (cfg.dirtrans) {
+        impl->enable_dirtrans(grid->g);   // refuses what the direct transform does not support, naming it
+    }
+    return new atlas_amd_Trans{impl.release(), grid};
     AA_CATCH_PTR
 }
 atlas_amd_Trans* atlas_amd__Trans__new(const atlas_amd_Grid* grid, int truncation) {
@@ -705,8 +723,44 @@ static int not_implemented(const char* what) {
                               " (TransLocal does not implement it either, TransLocal.cc:848-857,899-927,1599-1685)");
     return 2;
 }
-int atlas_amd__Trans__dirtrans_scalar(atlas_amd_Trans*, int, const double[], double[]) {
-    return not_implemented("dirtrans");
+// the direct transform is an extension on objects built with dirtrans=1; every other object (and a null handle) answers as TransLocal
+static int dirtrans_not_enabled() {
+    atlas_amd::set_last_error("Not implemented: dirtrans (build the Trans with dirtrans=1; TransLocal does not implement it, "
+                              "TransLocal.cc:848-857,899-927)");
+    return 2;
+}
+static bool dirtrans_enabled(const atlas_amd_Trans* t) {
+    return t && t->impl && t->impl->dirtrans_enabled();
+}
+int atlas_amd__Trans__dirtrans_scalar(atlas_amd_Trans* t, int nb_fields, const double gp_fields[], double scalar_spectra[]) {
+    if (!dirtrans_enabled(t)) {
+        return dirtrans_not_enabled();
+    }
+    AA_TRY
+    checked_call(t, "dirtrans_scalar", nb_fields, gp_fields, 0, nullptr, nullptr, scalar_spectra)
+        .dirtrans(nb_fields, gp_fields, scalar_spectra);
+    AA_CATCH_INT
+}
+int atlas_amd__Trans__dirtrans_scalar_device(atlas_amd_Trans* t, int nb_fields, const double* gp_fields_dev,
+                                             double* scalar_spectra_dev) {
+    if (!dirtrans_enabled(t)) {
+        return dirtrans_not_enabled();
+    }
+    AA_TRY
+    checked_call(t, "dirtrans_scalar_device", nb_fields, gp_fields_dev, 0, nullptr, nullptr, scalar_spectra_dev)
+        .dirtrans_scalar_device(nb_fields, gp_fields_dev, scalar_spectra_dev);
+    AA_CATCH_INT
+}
+int atlas_amd__Trans__timings_dirtrans(atlas_amd_Trans* t, double out[4], int reset) {
+    if (!dirtrans_enabled(t)) {
+        return dirtrans_not_enabled();
+    }
+    AA_TRY
+    if (!out) {
+        throw std::invalid_argument("Trans::timings_dirtrans: NULL output");
+    }
+    t->impl->dirtrans_timings(out, reset != 0);
+    AA_CATCH_INT
 }
 int atlas_amd__Trans__dirtrans_wind2vordiv(atlas_amd_Trans*, int, const double[], double[], double[]) {
     return not_implemented("dirtrans_wind2vordiv");
@@ -877,11 +931,36 @@ int atlas_amd__Trans__invtrans_vordiv2wind_adj_field(atlas_amd_Trans*, const atl
                                                      atlas_amd_Field*) {
     return not_implemented("invtrans_vordiv2wind_adj");
 }
-int atlas_amd__Trans__dirtrans_field(atlas_amd_Trans*, const atlas_amd_Field*, atlas_amd_Field*) {
-    return not_implemented("dirtrans");
+int atlas_amd__Trans__dirtrans_field(atlas_amd_Trans* t, const atlas_amd_Field* gpfield, atlas_amd_Field* spfield) {
+    if (!dirtrans_enabled(t)) {
+        return dirtrans_not_enabled();
+    }
+    AA_TRY
+    require_rank1(gpfield, "gpfield");
+    require_rank1(spfield, "spfield");
+    if (gpfield->shape[0] < (long)t->impl->nb_gridpoints_global() ||
+        (size_t)spfield->shape[0] < t->impl->nb_spectral_coefficients()) {
+        throw std::invalid_argument("dirtrans(Field, Field): field shorter than the grid / spectral size");
+    }
+    t->impl->dirtrans(1, gpfield->data, spfield->data);
+    AA_CATCH_INT
 }
-int atlas_amd__Trans__dirtrans_fieldset(atlas_amd_Trans*, const atlas_amd_Field*, int, atlas_amd_Field*, int) {
-    return not_implemented("dirtrans");
+int atlas_amd__Trans__dirtrans_fieldset(atlas_amd_Trans* t, const atlas_amd_Field* gpfields, int nb_gpfields,
+                                        atlas_amd_Field* spfields, int nb_spfields) {
+    if (!dirtrans_enabled(t)) {
+        return dirtrans_not_enabled();
+    }
+    if (nb_gpfields != nb_spfields || nb_gpfields < 0 || (nb_gpfields > 0 && (!gpfields || !spfields))) {
+        atlas_amd::set_last_error("dirtrans(FieldSet, FieldSet): gpfields.size() != spfields.size() or NULL field array");
+        return 1;
+    }
+    for (int f = 0; f < nb_gpfields; ++f) {
+        const int rc = atlas_amd__Trans__dirtrans_field(t, gpfields + f, spfields + f);
+        if (rc) {
+            return rc;
+        }
+    }
+    return 0;
 }
 int atlas_amd__Trans__dirtrans_wind2vordiv_field(atlas_amd_Trans*, const atlas_amd_Field*, atlas_amd_Field*,
                                                  atlas_amd_Field*) {

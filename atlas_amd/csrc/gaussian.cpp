@@ -271,5 +271,44 @@ StructuredGrid make_reduced_gaussian_grid(int N, const int pl[], int npl) {
     return g;
 }
 
+int gaussian_number(const StructuredGrid& g) {
+    if (g.N > 0) {
+        return g.ny() == 2 * g.N ? g.N : 0;
+    }
+    const int N = g.ny() / 2;
+    if (N < 1 || g.ny() != 2 * N || N > kMaxGaussianN) {
+        return 0;
+    }
+    std::vector<double> lat(2 * (size_t)N);
+    gaussian_latitudes_npole_spole(N, lat.data());
+    for (int j = 0; j < 2 * N; ++j) {
+        if (!(std::abs(lat[j] - g.y[j]) <= 1e-9)) {
+            return 0;
+        }
+    }
+    return N;
+}
+
+void gaussian_weights(const StructuredGrid& g, double w[]) {
+    const int N = gaussian_number(g);
+    if (N <= 0) {
+        throw std::invalid_argument("gaussian_weights: '" + g.name + "' is not a global Gaussian grid (2N latitudes of a Gaussian number N)");
+    }
+    const int n           = 2 * N;
+    const long double pi  = 3.14159265358979323846264338327950288L;
+    for (int j = 0; j < n; ++j) {
+        const long double x = sinl((long double)g.y[j] * (pi / 180.0L));
+        long double p0 = 1.0L, p1 = x;   // P_{k-1}, P_k by the three-term recurrence up to k = 2N
+        for (int k = 2; k <= n; ++k) {
+            const long double p2 = ((2 * k - 1) * x * p1 - (k - 1) * p0) / k;
+            p0                   = p1;
+            p1                   = p2;
+        }
+        // (1 - x^2) P'_n(x) = n (P_{n-1} - x P_n)
+        const long double d = n * (p0 - x * p1);
+        w[j]                = (double)(2.0L * (1.0L - x * x) / (d * d));
+    }
+}
+
 }  // namespace grid
 }  // namespace atlas_amd

@@ -45,5 +45,12 @@ StructuredGrid make_gaussian_grid(const std::string& name);
 // reduced Gaussian grid from an explicit pl array (N or 2N entries), e.g. a classic N<N> grid
 StructuredGrid make_reduced_gaussian_grid(int N, const int pl[], int npl);
 
+// Gaussian number of a grid: g.N for the grids made by name, else N = ny / 2 if the latitudes are the 2N Gaussian latitudes of N
+// (within 1e-9 degrees: a grid given by its rows and latitudes, e.g. Atlas's own); 0: not a global Gaussian grid
+int gaussian_number(const StructuredGrid& g);
+// Gaussian quadrature weights w_j = 2 / ((1 - mu_j^2) P'_2N(mu_j)^2) at the grid's OWN latitudes (mu_j = sin y_j), evaluated in
+// long double; they sum to 2.  Throws for a grid that is not a global Gaussian grid (gaussian_number(g) == 0).
+void gaussian_weights(const StructuredGrid& g, double w[]);
+
 }  // namespace grid
 }  // namespace atlas_amd

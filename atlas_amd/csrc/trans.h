@@ -16,6 +16,7 @@
 
 #include <cstddef>
 #include <cstdint>
+#include <memory>
 #include <string>
 #include <vector>
 
@@ -46,7 +47,10 @@ struct TransConfig {
                                       // wrapping around (a RectangularDomain crop, TransLocal.cc:1120-1135); empty: whole rows
     int device_tables          = -1;  // Legendre table computed on the device (1) or on the host and uploaded (0);
                                       // -1: environment variable ATLAS_AMD_TABLES=device|host, default device
+    bool dirtrans              = false;  // the direct transform (trans_dir.hip) is wanted: the caller runs enable_dirtrans()
 };
+
+struct DirTransState;   // trans_dir.hip
 
 struct StageTimings {
     double legendre_ms = 0, fourier_ms = 0;
@@ -121,6 +125,18 @@ public:
     // [u fields][v fields][scalar fields]; vor/div -> U,V in spectral space, truncation extended to T+1
     void invtrans_device(int nb_scalar_fields, const double* sp_dev, int nb_vordiv_fields, const double* vor_dev,
                          const double* div_dev, double* gp_dev);
+
+    // ---- direct transform of scalar fields (an extension: TransLocal does not implement dirtrans), trans_dir.hip ----
+    // enable_dirtrans() validates the object (global Gaussian grid, single device, whole grid, every row within a CU's LDS), keeps
+    // the Gaussian weights and builds the launch plans of the two stages; it throws naming what is not supported
+    void enable_dirtrans(const grid::StructuredGrid& grid);
+    bool dirtrans_enabled() const { return dir_ != nullptr; }
+    // gp[f*npts + rowoff(j) + i] -> sp[(2*pos(m,n) + imag)*nf + f] (the layouts invtrans writes / reads); asynchronous on stream()
+    void dirtrans_scalar_device(int nb_fields, const double* gp_dev, double* sp_dev);
+    void dirtrans(int nb_fields, const double gp_fields[], double scalar_spectra[]);   // host pointers (synchronous)
+    // profile=1: {Fourier stage ms, calls, Legendre stage ms, calls} of the direct transforms since the last reset
+    void dirtrans_timings(double out[4], bool reset);
+    const std::vector<double>& gaussian_weights() const;
 
     // ---- host-pointer API (synchronous) : TransLocal.cc:931-934, 1486-1490, 1523-1597 ----
     void invtrans(int nb_scalar_fields, const double scalar_spectra[], double gp_fields[]);
@@ -295,6 +311,7 @@ private:
     std::vector<int> ev_kind_;        // 0 legendre, 1 fourier, per pair
     size_t ev_used_ = 0;
     StageTimings timings_;
+    std::shared_ptr<DirTransState> dir_;   // direct transform plans and buffers (null: not enabled)
 };
 
 }  // namespace trans

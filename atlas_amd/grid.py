@@ -65,6 +65,12 @@ class StructuredGrid:
     def regular(self):
         return bool(_lib.Grid_regular(self._h))
 
+    def gaussian_weights(self):
+        """Gaussian quadrature weights at the grid's own latitudes (ny values, north to south, sum 2); global Gaussian grids only"""
+        out = np.zeros(self.ny())
+        _lib.check(_lib.Grid_gaussian_weights(self._h, out.ctypes.data))
+        return out
+
 
 def Grid(name):
     """atlas::Grid("F64") / Grid("O1280")"""

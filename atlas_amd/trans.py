@@ -207,7 +207,19 @@ class Trans:
         _lib.check(_lib.Trans_invtrans_adj_field(self._h, None, None))
 
     def dirtrans_field(self, gpfield, spfield):
-        _lib.check(_lib.Trans_dirtrans_field(self._h, None, None))
+        """dirtrans(const Field& gpfield, Field& spfield) on an object built with dirtrans=1 (rank-1 fields; an extension)"""
+        self._dirtrans_enabled()
+        _lib.check(_lib.Trans_dirtrans_field(self._h, self._field(gpfield, "gpfield"),
+                                             self._field(spfield, "spfield", True)))
+        return spfield
+
+    def dirtrans_fieldset(self, gpfields, spfields):
+        """dirtrans(const FieldSet& gpfields, FieldSet& spfields) on an object built with dirtrans=1 (an extension)"""
+        self._dirtrans_enabled()
+        gp = (_lib.Field * max(len(gpfields), 1))(*[self._field(a, "gpfields[]") for a in gpfields])
+        sp = (_lib.Field * max(len(spfields), 1))(*[self._field(a, "spfields[]", True) for a in spfields])
+        _lib.check(_lib.Trans_dirtrans_fieldset(self._h, gp, len(gpfields), sp, len(spfields)))
+        return spfields
 
     # ---- backend registry (Trans.cc:37-48) ----
     @staticmethod
@@ -231,9 +243,36 @@ class Trans:
         """TransLocal.cc:1486-1490 (pointer API)"""
         return self.invtrans(0, None, nb_fields, vorticity_spectra, divergence_spectra, wind_fields)
 
-    # ---- not implemented by TransLocal (TransLocal.cc:848-857,899-927,1599-1685) ----
+    # ---- direct transform (an extension on objects built with dirtrans=1; TransLocal.cc:848-857,899-927 do not implement it) ----
+    def _dirtrans_enabled(self):
+        # the library answers first: "Not implemented" (NotImplementedError) on an object built without dirtrans=1
+        _lib.check(_lib.Trans_dirtrans_scalar(self._h, 0, None, None))
+
     def dirtrans(self, nb_fields, scalar_fields, scalar_spectra):
-        _lib.check(_lib.Trans_dirtrans_scalar(self._h, nb_fields, None, None))
+        """dirtrans(nb_fields, gp, sp): grid points in invtrans's output layout -> spectra in its input layout.  numpy arrays go
+        through the host-pointer entry point, torch device tensors through the device one (stream-ordered like invtrans)"""
+        self._dirtrans_enabled()
+        nf = int(nb_fields)
+        ncoef, npts = self.nb_spectral_coefficients(), self.nb_gridpoints_global()
+        dev = _is_device(scalar_fields)
+        if dev != _is_device(scalar_spectra):
+            raise TypeError("grid-point and spectral arrays must both be host or both be device")
+        gp_p = _ptr(scalar_fields, npts * nf, "scalar_fields")
+        sp_p = _ptr(scalar_spectra, ncoef * nf, "scalar_spectra", writable=True)
+        if dev:
+            with _lib.torch_stream_order(self.stream()):
+                _lib.check(_lib.Trans_dirtrans_scalar_device(self._h, nf, gp_p, sp_p))
+        else:
+            _lib.check(_lib.Trans_dirtrans_scalar(self._h, nf, gp_p, sp_p))
+        return scalar_spectra
+
+    def timings_dirtrans(self, reset=False):
+        """profile=1: accumulated stage times of the direct transforms"""
+        out = (C.c_double * 4)()
+        _lib.check(_lib.Trans_timings_dirtrans(self._h, out, int(reset)))
+        return {"fourier_ms": out[0], "fourier_calls": int(out[1]), "legendre_ms": out[2], "legendre_calls": int(out[3])}
+
+    # ---- not implemented by TransLocal (TransLocal.cc:848-857,899-927,1599-1685) ----
 
     def dirtrans_wind2vordiv(self, nb_fields, wind, vor, div):
         _lib.check(_lib.Trans_dirtrans_wind2vordiv(self._h, nb_fields, None, None, None))

@@ -94,6 +94,9 @@ int atlas_amd__Grid__y(const atlas_amd_Grid* g, double lat_deg_out[]);
 /* Gaussian latitudes north pole -> south pole, 2N values
  * (src/atlas/grid/detail/spacing/gaussian/Latitudes.cc:41-67) */
 int atlas_amd__gaussian_latitudes_npole_spole(int N, double lats_out[]);
+/* Gaussian quadrature weights w_j = 2 / ((1 - mu_j^2) P'_2N(mu_j)^2) at the grid's own latitudes (ny values, sum 2); an error for a
+ * grid that is not a global Gaussian grid */
+int atlas_amd__Grid__gaussian_weights(const atlas_amd_Grid* g, double weights_out[]);
 
 /* ---------------------------------------------------------------------------------------------------------------
  * Trans.  Replaces atlas__Trans__* (src/atlas/trans/detail/TransInterface.h:44-107) for type "local".
@@ -122,6 +125,9 @@ atlas_amd_Trans* atlas_amd__Trans__new(const atlas_amd_Grid* grid, int truncatio
  *   tables=host|device   where the Legendre table is computed when no cache is given: on the host (OpenMP, then
  *                        uploaded) or on the device from O(T^2) host-prepared inputs (bit-identical; default: the
  *                        environment variable ATLAS_AMD_TABLES, else device: 0.9 s against 6.7 s at TL1279)
+ *   dirtrans=0|1         1: the object also runs the direct transform of scalar fields (atlas_amd__Trans__dirtrans_scalar*,
+ *                        an extension TransLocal lacks).  Global Gaussian grids on a single-device object only: non-Gaussian
+ *                        grids, rows= / domain= crops, nparts > 1 and rows beyond a CU's LDS are refused here, by name
  * legendre_cache / size: optional Legendre cache blob in TransLocal's file layout (TransLocal.cc:608-614), or NULL */
 atlas_amd_Trans* atlas_amd__Trans__new_config(const atlas_amd_Grid* grid, int truncation, const char* config,
                                               const void* legendre_cache, size_t legendre_cache_size);
@@ -198,10 +204,22 @@ int atlas_amd__Trans__invtrans_device_f32(atlas_amd_Trans* t, int nb_scalar_fiel
                                           int nb_vordiv_fields, const float* vorticity_spectra_dev,
                                           const float* divergence_spectra_dev, float* gp_fields_dev);
 
-/* direct transforms and adjoints: not implemented by TransLocal either (TransLocal.cc:848-857,899-927,1599-1685);
- * these return an error whose message starts with "Not implemented" */
+/* direct transform of scalar fields: an extension on objects built with dirtrans=1 (TransLocal does not implement it,
+ * TransLocal.cc:848-857,899-927).  gp in invtrans's output layout gp[f*npts + rowoff(j) + i], sp in its input layout
+ * sp[(2*pos(m,n) + imag)*nf + f]; per row j the Fourier coefficients F_m = (1/n_j) sum_i x_i exp(-i m lambda_i) for m <= M_j (the
+ * inverse's Fourier truncation), then a_n^m = 1/2 sum_j w_j P_n^m(mu_j) F_m(j) with Gaussian weights w_j: dirtrans(invtrans(s)) = s
+ * where the quadrature is exact.  All m <= T are written (m = T too), Im a_n^0 = 0.  A field's result does not depend on nb_fields
+ * or on the entry point (bitwise).  On any other object (and on a null handle) these answer "Not implemented: dirtrans ..." */
 int atlas_amd__Trans__dirtrans_scalar(atlas_amd_Trans* t, int nb_fields, const double scalar_fields[],
                                       double scalar_spectra[]);
+/* the same on device pointers, asynchronous on the Trans stream; no allocation or synchronisation after the first call of a
+ * shape (graph capture as invtrans) */
+int atlas_amd__Trans__dirtrans_scalar_device(atlas_amd_Trans* t, int nb_fields, const double* gp_fields_dev,
+                                             double* scalar_spectra_dev);
+/* profile=1: out = {fourier_ms, fourier_calls, legendre_ms, legendre_calls} of the direct transforms; reset != 0 clears them */
+int atlas_amd__Trans__timings_dirtrans(atlas_amd_Trans* t, double out[4], int reset);
+/* adjoints and dirtrans_wind2vordiv: not implemented by TransLocal either (TransLocal.cc:848-857,899-927,1599-1685); these return an
+ * error whose message starts with "Not implemented" */
 int atlas_amd__Trans__dirtrans_wind2vordiv(atlas_amd_Trans* t, int nb_fields, const double wind_fields[],
                                            double vorticity_spectra[], double divergence_spectra[]);
 int atlas_amd__Trans__invtrans_adj_scalar(atlas_amd_Trans* t, int nb_fields, const double gp_fields[],
